@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/sec of the 3-modality UGaitNet hot path, forward + backward + Adam, on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[2], SURVEY.md section 8d "C3"): 3 modalities (optical flow 2ch + gray + depth),
 25 frames of 60x60, 24 clips per GPU, 12 ids x 2, 150 classes, sign_max fusion with the 7-pattern missing-modality
@@ -165,7 +165,41 @@ def build_parser():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and run the gradient collectives even with one rank (rehearses the RCCL "
                          "code path on a one-GPU box)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(rank 0; float32 / float64, at most 64 MB; see dump_outputs)")
     return ap
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024     # elements kept of each flat parameter / gradient buffer (16 MB each in float32)
+
+
+def dump_outputs(core, losses, out_dir):
+    """The arrays a caller of GaitCore.train_step receives after the last timed step, as DIR/<name>.npy:
+    signature [62, B, 256], triplet_loss_per_bin [62], class_probabilities [B, ncls] and xent_per_clip [B] (when the model has a
+    head), losses = [loss, triplet, xent, acc] (float64), and the flat parameter buffer after Adam and the flat gradient buffer of
+    the step (`params`, `grads`): each in full when it holds at most DUMP_SAMPLE elements, otherwise the elements at a fixed
+    sorted index set drawn with numpy seed 0 (the same on every run of the same workload).  64 MB in all at most."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def sample(t):
+        if t.numel() <= DUMP_SAMPLE:
+            return t
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        return t[torch.from_numpy(idx).to(t.device)]
+    arrays = dict(signature=core.sig, triplet_loss_per_bin=core.bin_loss)
+    if core.nclasses > 0:
+        arrays.update(class_probabilities=core.head["probs"], xent_per_clip=core.head["row_loss"])
+    arrays.update(params=sample(core.store.flat), grads=sample(core.store.grad))
+    out = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    out["losses"] = np.array([losses.get(k, np.nan) for k in ("loss", "triplet", "xent", "acc")], np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the 64 MB limit" % total)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def launch_ranks(args, argv):
@@ -491,6 +525,8 @@ def run(args):
         ctx.__exit__(None, None, None)
     losses = core.losses()
     grad_bytes = int(core.store.numel * 4)
+    if args.dump_outputs and rank == 0:      # (before the roofline pass: it runs further steps on the same core)
+        dump_outputs(core, losses, args.dump_outputs)
 
     roof = None
     if not args.no_roofline_pass:

@@ -14,13 +14,18 @@ is checked against files it did not write itself.
   float64 / int8 datasets, chunked datasets with edge chunks and fletcher32, fixed- and variable-length string attributes.
 * latest.h5              -- the same kind of content written with libver='latest' (what the reader takes of it, and what it refuses).
 The expected contents are stored beside each file as <name>.npz by this script (read back through h5py).
+* writer_output.h5       -- the file ugaitnet_amd/h5lite.py's Writer makes of `writer_case()`, stored only after the HDF5 library has
+  read it back and found every dataset and attribute (`check_with_library`); tests/test_h5lite.py requires the writer to reproduce
+  it byte for byte.  `... make_h5_fixtures.py writer` rewrites this file alone.
 """
 import os
 import sys
 
-import h5py
 import numpy as np
 
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "h5")
 os.makedirs(OUT, exist_ok=True)
 rng = np.random.default_rng(2323)
@@ -68,7 +73,49 @@ def write_keras_weights(g, layers, expect, prefix=""):
             expect[prefix + name + "/" + w] = val
 
 
+def writer_case():
+    """(h5lite Writer, {dataset path: expected array}): more than one symbol-table node, names that sort differently from their
+    creation order, integer / float64 / scalar datasets, root, group and dataset attributes."""
+    from ugaitnet_amd import h5lite
+    rng = np.random.default_rng(5)
+    w = h5lite.Writer()
+    exp = {}
+    for i in range(70):
+        k = "g%d/layer_%d/kernel:0" % (i % 3, 70 - i)
+        exp[k] = rng.standard_normal((2, 3)).astype(np.float32)
+        w.create_dataset(k, exp[k])
+    exp["i16"] = np.int16([[1, -2], [3, 4]])
+    exp["f64"] = np.float64([0.25])
+    exp["u8s"] = np.uint8(200)
+    for k in ("i16", "f64", "u8s"):
+        w.create_dataset(k, exp[k])
+    w.set_attr("", "layer_names", [b"alpha", b"be", b"gamma_long_name"])
+    w.set_attr("g1", "count", np.int32(3))
+    w.set_attr("i16", "unit", "px")
+    return w, exp
+
+
+def check_with_library(h5py, path, exp):
+    """The HDF5 library (h5py) reads the writer's file at `path` and finds exactly `writer_case()`'s content."""
+    with h5py.File(path, "r") as f:
+        assert all(np.array_equal(f[k][()], e) and f[k].dtype == e.dtype and f[k].shape == e.shape for k, e in exp.items())
+        assert list(f.attrs["layer_names"]) == [b"alpha", b"be", b"gamma_long_name"]
+        assert f["g1"].attrs["count"] == 3 and f["i16"].attrs["unit"] == b"px"
+        n = []
+        f.visit(n.append)
+        assert sum(isinstance(f[k], h5py.Dataset) for k in n) == len(exp)
+
+
+def write_writer_fixture():
+    import h5py
+    w, exp = writer_case()
+    path = os.path.join(OUT, "writer_output.h5")
+    w.save(path)
+    check_with_library(h5py, path, exp)
+
+
 def main():
+    import h5py
     layers = keras_layers()
     exp = {}
     with h5py.File(os.path.join(OUT, "keras_weights_small.h5"), "w") as f:
@@ -153,8 +200,12 @@ def main():
         f.create_dataset("chunked", data=np.arange(100, dtype=np.int16).reshape(10, 10), chunks=(4, 4), compression="gzip")
         for i in range(20):
             f.create_dataset("many/d%d" % i, data=np.float32(i))
+    write_writer_fixture()
     print("wrote", sorted(os.listdir(OUT)))
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    if sys.argv[1:] == ["writer"]:
+        write_writer_fixture()
+    else:
+        sys.exit(main())

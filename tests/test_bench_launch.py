@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -162,3 +163,29 @@ def test_other_fp32_class_lines_beside_the_headline(dev):
     assert ra["bound"] in ("mfma", "hbm") and 0.05 < ra["frac"] <= 1.0 and ra["stalled_launches"] == 0
     # the serialised pass is queued behind a gate (no event pair contains host time) and reports what it drops
     assert d["roofline"]["stalled_launches"] == 0 and d["roofline"]["gate"]["spin_ms"] >= d["roofline"]["gate"]["host_ms_per_profiled_step"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_dump_outputs_of_the_last_timed_step(dev, tmp_path):
+    """--dump-outputs DIR writes the last timed step's results as float32 / float64 .npy files, 64 MB at most; `steps` and
+    `ms_per_step` describe the timed steps; two runs with the same arguments start from the same inputs and weights."""
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--dense-only",
+                            "--no-roofline-pass", "--clips-per-gpu", "8", "--dump-outputs", str(out)],
+                           env=_env(), capture_output=True, text=True, timeout=800)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 8) < 0.05
+        got = {p.stem: np.load(str(p)) for p in out.glob("*.npy")}
+        assert set(got) == {"signature", "triplet_loss_per_bin", "class_probabilities", "xent_per_clip", "losses", "params", "grads"}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+        assert got["signature"].shape == (62, 8, 256) and got["class_probabilities"].shape == (8, 150)
+        assert abs(got["losses"][0] - d["loss"]) < 1e-4
+        dumps.append(got)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[0][k], dumps[1][k], rtol=1e-4, atol=1e-6, err_msg=k)

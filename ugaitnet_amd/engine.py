@@ -84,6 +84,10 @@ class _Launch:
     def join_backward_streams(self):
         """The current stream waits for every backward chain and weight gradient issued so far."""
         cur = torch.cuda.current_stream(self.device)
+        if torch.cuda.is_current_stream_capturing():
+            # (a captured step runs on one stream, GraphedTrainStep: a wait on a stream outside the capture would put an event recorded
+            #  outside the graph into it)
+            return
         for st in list(self.bstream.values()) + list(self.wstream.values()):
             cur.wait_stream(st)
 
@@ -696,7 +700,9 @@ class GaitCore:
     def join_pack(self):
         """The current stream waits for the filter repack queued by the last apply_gradients, if one is outstanding."""
         ev = self._pack_event
-        if ev is not None:      # (kept until the NEXT pack replaces it: a consumer on another stream must wait for it too -- ADVICE r04)
+        # (kept until the NEXT pack replaces it: a consumer on another stream must wait for it too -- ADVICE r04.  Not while a graph is
+        #  captured: the event was recorded outside the graph, and weights_changed() drops it during the capture of the update graph)
+        if ev is not None and not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(self.device).wait_event(ev)
 
     def _before_conv3(self):
@@ -1131,8 +1137,10 @@ class GraphedTrainStep:
 
     A step is ~150 kernel launches; at 24 clips per GPU the GPU needs 9 ms for them and the host 2 ms, but at 4-8 clips (the
     8-GPU split of the reference's 40-clip batch is 5 per GPU) the launches themselves set the pace.  Replaying a graph removes
-    the per-launch host cost; the arithmetic, the kernels and the two-stream dependency structure (captured as graph edges) are
-    exactly those of `GaitCore.train_step`, so parameters stay bit-identical (tests/test_graph_gpu.py).
+    the per-launch host cost; the arithmetic and the kernels are exactly those of `GaitCore.train_step`, so parameters stay
+    bit-identical (tests/test_graph_gpu.py).  Both graphs are captured with every launch on ONE stream (`serial_launches`: results
+    unchanged) and hold nothing but their own kernel and memset nodes in one chain: no side-stream branches, and no wait on an
+    event recorded outside the capture (the filter-pack event of an eager step is joined by `step()` before the replays).
 
     The graph is captured for ONE batch geometry: shapes, the equality structure of the labels (which rows share an identity
     -- what the triplet index lists depend on; the sampler's P x K batches all share it) and dense encoders (no skip_masked).
@@ -1157,8 +1165,7 @@ class GraphedTrainStep:
         cur = torch.cuda.current_stream(dev)
         warm = torch.cuda.Stream(device=dev)
         warm.wait_stream(cur)
-        fwd_streams, core.cfg.fwd_streams = core.cfg.fwd_streams, 0     # the captured forward pass is one chain (the backward keeps its two streams)
-        try:
+        with core.serial_launches():      # (warm-up in the configuration of the capture: the same buffers and function attributes)
             with torch.cuda.stream(warm):   # allocations, function attributes, triplet lists: all outside the capture
                 for _ in range(2):
                     core.forward_backward(self.xs, self.uses, self.labels, self.onehot)
@@ -1168,15 +1175,13 @@ class GraphedTrainStep:
             self.g_fb = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_fb):
                 core.forward_backward(self.xs, self.uses, self.labels, self.onehot)
-        finally:
-            core.cfg.fwd_streams = fwd_streams
-        core._ar_pending = None     # (bucket all-reduces are not captured: the reduction runs between the two graphs)
-        scale = (1.0 / core.world) if core.world > 1 else 1.0
-        self.g_up = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_up):
-            ops.adam_step_dev(core.store.flat, core.store.grad, core.store.m, core.store.v, self.lr, core.beta_1, core.beta_2,
-                              core.epsilon, scale)
-            core.weights_changed()
+            core._ar_pending = None     # (bucket all-reduces are not captured: the reduction runs between the two graphs)
+            scale = (1.0 / core.world) if core.world > 1 else 1.0
+            self.g_up = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_up):
+                ops.adam_step_dev(core.store.flat, core.store.grad, core.store.m, core.store.v, self.lr, core.beta_1, core.beta_2,
+                                  core.epsilon, scale)
+                core.weights_changed()
 
     @staticmethod
     def _pattern(labels):
@@ -1195,6 +1200,7 @@ class GraphedTrainStep:
                 dst.copy_(core._dev(src).reshape(dst.shape), non_blocking=True)
         if self.onehot is not None:
             self.onehot.copy_(core._dev(onehot).reshape(self.onehot.shape), non_blocking=True)
+        core.join_pack()      # (a filter repack an eager step of this core left on the second stream: the graphs do not wait for it)
         self.g_fb.replay()
         if core.world > 1:
             dp.allreduce_sum_(core.store.grad, core.pg)
