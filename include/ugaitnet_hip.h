@@ -248,6 +248,24 @@ int ugn_assemble_modality(const void* raw, int is_int16, const int32_t* src_row,
                           float offset, float post_mul, float clip_max, float clip_min, float noise, float* x_out,
                           float* flag_out, void* stream);
 
+/* The same assembly with the training generator's random affine / mirror augmentation (`augmentation_x > 0`,
+ * data/mj_augmentation.py): every transformed base sample is decoded, warped (bilinear, edge-clamped, through the record's row /
+ * column tap tables), for the non-OF generator channel-shifted and brightness-quantised, range-fixed and mirrored ONCE into `ws`;
+ * rows copy it from there.  An untransformed base sample decodes exactly as ugn_assemble_modality does.
+ * nbase: base samples in `raw` (every src_row entry must be < nbase; the caller checks).
+ * aug: device int32 [nbase][UGN_AUG_RECORD_WORDS], one record per base sample:
+ *   [0] transformed 0/1, [1] non-OF generator (channel shift + brightness) 0/1, [2] mirrored 0/1, [3] clip_max, [4] clip_min,
+ *   [5] channel shift, [6] brightness (floats stored bitwise), [7] unused,
+ *   [8..67] row tap index, [68..127] row tap weight (float), [128..187] column tap index, [188..247] column tap weight (float):
+ *   out[r][c] = bilinear of the decoded frame at rows (i, i+1) with weights (1-w, w), clamped to the frame.
+ * The clip of a record applies to int16 data only and to transformed and untransformed samples alike.
+ * ws: device scratch of ugn_assemble_modality_aug_ws(nbase, channels) bytes.  Three launches on `stream`, no host synchronisation. */
+#define UGN_AUG_RECORD_WORDS 248
+size_t ugn_assemble_modality_aug_ws(int nbase, int channels);
+int ugn_assemble_modality_aug(const void* raw, int is_int16, const int32_t* src_row, int nrows, int nbase, int channels,
+                              float divisor, float offset, float post_mul, float noise, const int32_t* aug, float* ws,
+                              size_t ws_bytes, float* x_out, float* flag_out, void* stream);
+
 /* Row gather / scatter of the mask-skipping step: a masked (clip, modality) pair is multiplied by 0 in the gate
  * (nets/mj_uwyhNets_ba.py:51-54), so a modality's encoder may run on the clips whose flag is 1 only.  t = [outer][rows][row_floats]
  * fp32, idx [nidx] int64 (device) row numbers, row_floats a multiple of 4, 16-byte aligned pointers.

@@ -4,7 +4,12 @@ that arrive as HOST numpy arrays from a keras.utils.Sequence-shaped generator --
 against bench.py's device-resident step.  Prints one line per mode:
     plain   workers=0, pipeline=False: fetch, copy, step, read the losses, one after the other
     piped   the defaults (workers=1, max_queue_size=10, losses one step late): what tf.keras's fit does for a Sequence
-usage: python tools/bench_fit.py [--clips 24] [--steps 30] [--host-ms 0] [--workers 1]   (--host-ms: extra host work per generator call)"""
+With --augment the generator is the device-assembling one instead (raw int16 / uint8 samples uploaded per batch, decoded, expanded
+and masked by DeviceBatchAssembler, as ugaitnet_amd.sampler.DeviceDataGenerator does), and the lines are
+    assembled   that generator with the reference's augmentation_x=0
+    augmented   the same with augmentation_x > 0: random affine / mirror augmentation drawn per batch (ugaitnet_amd/augment.py)
+usage: python tools/bench_fit.py [--clips 24] [--steps 30] [--host-ms 0] [--workers 1] [--augment]
+(--host-ms: extra host work per generator call)"""
 import argparse
 import os
 import sys
@@ -21,6 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--host-ms", type=float, default=0.0)
     ap.add_argument("--workers", type=int, default=1)
+    ap.add_argument("--augment", action="store_true", help="device-assembled batches, without and with the augmentation")
     args = ap.parse_args()
     import torch
     from tests.synth import make_batch
@@ -48,12 +54,48 @@ def main():
         def on_epoch_end(self):
             pass
 
+    class DeviceGen:
+        """C3 batches of `clips` rows (base samples x expand 3) assembled on the device from raw samples, augmented or not"""
+        def __init__(self, augment):
+            import random
+            from ugaitnet_amd import augment as A
+            from ugaitnet_amd.batching import DeviceBatchAssembler, ModalitySpec, plan_rows
+            self.A, self.plan_rows, self.augment, self.expand = A, plan_rows, augment, 3
+            self.nbase = args.clips // self.expand
+            rng = np.random.default_rng(7)
+            self.raws = [rng.integers(-3000, 3000, (4, self.nbase, 60, 60, 50)).astype(np.int16),
+                         rng.integers(0, 256, (4, self.nbase, 60, 60, 25)).astype(np.uint8),
+                         rng.integers(0, 256, (4, self.nbase, 60, 60, 25)).astype(np.uint8)]
+            self.asm = DeviceBatchAssembler([ModalitySpec("of", 2, compress_factor=100.0), ModalitySpec("gray", 1), ModalitySpec("depth", 1)])
+            self.present = np.ones((self.nbase, 3), bool)
+            self.np_rng, self.mask_rng = np.random.RandomState(5), random.Random(5)
+            labels = np.repeat(np.arange(self.nbase) // 2, self.expand).astype(np.float32).reshape(-1, 1)
+            onehot = np.zeros((labels.shape[0], 150), np.float32)
+            onehot[np.arange(labels.shape[0]), labels[:, 0].astype(np.int64)] = 1.0
+            self.Y = [labels, onehot]
+
+        def __len__(self):
+            return 4
+
+        def __getitem__(self, i):
+            aug = self.A.draw_batch(self.nbase, True, self.np_rng) if self.augment else None
+            plan = self.plan_rows(self.present, self.expand, rng=self.mask_rng)
+            X = []
+            for x, u in self.asm.assemble([r[i] for r in self.raws], plan, present=self.present, aug=aug):
+                X += [x, u]
+            return X, self.Y
+
+        def on_epoch_end(self):
+            pass
+
     shapes = [(25, 60, 60, 2), (25, 60, 60, 1), (25, 60, 60, 1)]
-    for name, kw in (("plain", dict(workers=0, pipeline=False)), ("piped", dict(workers=args.workers)), ("plain", dict(workers=0, pipeline=False)),
-                     ("piped", dict(workers=args.workers))):
+    modes = (("plain", dict(workers=0, pipeline=False)), ("piped", dict(workers=args.workers))) * 2
+    if args.augment:
+        modes = (("assembled", dict(workers=args.workers)), ("augmented", dict(workers=args.workers))) * 2
+    for name, kw in modes:
         model = UWYHSemiNet3Mods.build_or_load(shapes, 4, [7, 5, 3, 2], [96, 192, 512, 4096], ndense_units=0, optimizer=optimizers.Adam(lr=1e-4),
                                                margin=0.2, nclasses=150, loss_weights=[1.0, 0.1], fMerge=sign_max, gaitset=True, seed=1)
-        gen = Gen()
+        gen = DeviceGen(name == "augmented") if args.augment else Gen()
         model.fit(gen, epochs=1, steps_per_epoch=5, verbose=0, **kw)       # warm-up: buffers, pinned pool, filter pack
         torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -75,6 +75,8 @@ PROTOTYPES = {
     "ugn_triplet_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _f, _i, _p]),
     "ugn_triplet_hard_fwd_bwd": (_i, [_p, _p, _f, _p, _p, _p, _f, _i, _p]),
     "ugn_assemble_modality": (_i, [_p, _i, _p, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p]),
+    "ugn_assemble_modality_aug_ws": (_sz, [_i, _i]),
+    "ugn_assemble_modality_aug": (_i, [_p, _i, _p, _i, _i, _i, _f, _f, _f, _f, _p, _p, _sz, _p, _p, _p]),
     "ugn_gather_rows": (_i, [_p, _p, _p, _i, _i, _i, _sz, _p]),
     "ugn_scatter_rows": (_i, [_p, _p, _p, _i, _i, _i, _sz, _p]),
     "ugn_knn_ws": (_sz, [_i, _i]),

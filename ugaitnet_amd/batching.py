@@ -4,7 +4,9 @@ The reference's generator (`data/mj_dataGeneratorMMUWYHsingle_repetitions.py`) d
 re-lays it out for the gaitset network and repeats it `expand` times with modalities disabled, all in float64 numpy, and
 ships the result to the GPU.  Here the host only decides WHICH rows exist (`plan_rows`, the same rules and the same
 `random` call sequence as `__gen_batchMM` :776-806); the raw int16 / uint8 sample arrays are uploaded once and
-`DeviceBatchAssembler` produces the fp32 `[rows,25,60,60,C]` tensors and `[rows,1]` flags in HBM (ugn_assemble_modality).
+`DeviceBatchAssembler` produces the fp32 `[rows,25,60,60,C]` tensors and `[rows,1]` flags in HBM (ugn_assemble_modality).  With
+`aug` (the draws of ugaitnet_amd/augment.py) the training generator's random affine / mirror augmentation runs in the same device
+assembly (ugn_assemble_modality_aug), once per base sample.
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import augment as _augment
 from ._lib import call, ptr
 
 NOISE = 0.000000001   # reference `self.noise` (:102)
@@ -95,14 +98,24 @@ class DeviceBatchAssembler:
         self.specs = list(specs)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
-    def assemble(self, raws, src, present=None, clip=(0.0, 0.0)):
+    def assemble(self, raws, src, present=None, clip=(0.0, 0.0), aug=None):
         """raws[m]: [nbase,60,60,25*C] int16/uint8 (numpy or device tensor); src: plan_rows output.
         present [nbase][nmods]: a copied-but-absent modality keeps flag 1 with a noise payload, exactly as the reference does.
         clip = (clip_max, clip_min) of the optical-flow augmentation (:723-728), applied to int16 modalities only.
-        Returns [(x_m [rows,25,60,60,C] fp32, u_m [rows,1] fp32)] on the device."""
+        aug: one augment.SampleAug per base sample (augment.draw_batch): the random affine / mirror augmentation, each sample with
+        its own clip (then `clip` must stay (0, 0)).  Returns [(x_m [rows,25,60,60,C] fp32, u_m [rows,1] fp32)] on the device."""
         src = np.asarray(src, np.int32)
         rows = src.shape[0]
         out = []
+        records = None
+        if aug is not None:
+            if tuple(clip) != (0.0, 0.0):
+                raise ValueError("with `aug` the clip is drawn per sample: pass clip=(0, 0)")
+            nbase = len(aug)
+            if present is not None and np.asarray(present).shape != (nbase, len(self.specs)):
+                raise ValueError("present must be [nbase][nmods] = [%d][%d]" % (nbase, len(self.specs)))
+            rec = _augment.pack_records(aug, len(self.specs), present, [s.is_int16 for s in self.specs])
+            records = torch.from_numpy(rec).to(self.device)      # (one upload for every modality of the batch)
         for m, spec in enumerate(self.specs):
             raw = raws[m]
             if not isinstance(raw, torch.Tensor):
@@ -127,10 +140,24 @@ class DeviceBatchAssembler:
             scol = torch.from_numpy(col).to(self.device)
             x = torch.empty((rows, 25, 60, 60, spec.channels), dtype=torch.float32, device=self.device)
             u = torch.empty((rows, 1), dtype=torch.float32, device=self.device)
+            if records is not None:
+                if raw.shape[0] != len(aug):
+                    raise ValueError("modality %d: %d base samples uploaded, %d augmentation draws" % (m, raw.shape[0], len(aug)))
+                nb = raw.shape[0]
+                ws_bytes = _lib.load().ugn_assemble_modality_aug_ws(nb, spec.channels)
+                ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=self.device)
+                call("ugn_assemble_modality_aug", ptr(raw), int(spec.is_int16), ptr(scol), rows, nb, spec.channels, spec.divisor,
+                     spec.offset, spec.post_mul, NOISE, ptr(records[m]), ptr(ws), ws_bytes, ptr(x), ptr(u),
+                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                out.append(self._fix_flags(x, u, flag_fix))
+                continue
             cmax, cmin = (clip if spec.is_int16 else (0.0, 0.0))
             call("ugn_assemble_modality", ptr(raw), int(spec.is_int16), ptr(scol), rows, spec.channels, spec.divisor, spec.offset,
                  spec.post_mul, float(cmax), float(cmin), NOISE, ptr(x), ptr(u), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if flag_fix is not None and flag_fix.any():
-                u[torch.from_numpy(np.nonzero(flag_fix)[0]).to(self.device)] = 1.0
-            out.append((x, u))
+            out.append(self._fix_flags(x, u, flag_fix))
         return out
+
+    def _fix_flags(self, x, u, flag_fix):
+        if flag_fix is not None and flag_fix.any():
+            u[torch.from_numpy(np.nonzero(flag_fix)[0]).to(self.device)] = 1.0
+        return x, u

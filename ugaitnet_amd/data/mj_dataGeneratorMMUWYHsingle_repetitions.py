@@ -2,16 +2,18 @@
 by ugaitnet_amd.sampler.DeviceDataGenerator: the mains' `DataGeneratorGaitMMUWYH(allSamples, ..., datadir=[...], labmap=...,
 gait=..., nmods=3, gaitset=True, repetition=r, expand_level=e)` keeps working and yields batches that already live in HBM.
 
-Implemented: the one-, two- and three-modality gaitset generators without augmentation (`nmods=1|2|3, gaitset=True,
-augmentation_x=0`), the label cycling of `__getitem__`, `__len__`, `on_epoch_end`, `keep_data`.  Everything else the
-reference's class can do (affine / mirror augmentation, sample weights, auxiliary / per-FC label lists, 3-D inputs, debug
-batches) raises NotImplementedError instead of silently producing different batches."""
+Implemented: the one-, two- and three-modality gaitset generators (`nmods=1|2|3, gaitset=True`) with `augmentation_x=0`, or with
+`augmentation_x > 0` (the reference's default: random affine / mirror augmentation) when the caller opts in with
+`device_augmentation=True` -- the augmentation then runs in the device assembly (ugaitnet_amd/augment.py); the label cycling of
+`__getitem__`, `__len__`, `on_epoch_end`, `keep_data`.  Everything else the reference's class can do (sample weights, auxiliary /
+per-FC label lists, 3-D inputs, debug batches) raises NotImplementedError instead of silently producing different batches."""
 from __future__ import annotations
 
 import os
 
 import numpy as np
 
+from .. import augment as _augment
 from ..batching import ModalitySpec
 from ..sampler import DeviceDataGenerator
 from .. import samples as _samples
@@ -22,20 +24,22 @@ class DataGeneratorGaitMMUWYH(DeviceDataGenerator):
                  augmentation=True, datadir=[], sess=None, labmap=[], gait=[], ntype=1, isTest=False, augmentation_x=1,
                  expand_level=2, balanced_classes=True, isTriplet=False, use3D=False, isDebug=False, softlabel=False, camera=[],
                  nmods=2, use_weights=False, meanSample=0.0, aux_losses=False, triplet_all_fc=False, nfcs=0, keep_data=False,
-                 gaitset=False, repetition=4):
+                 gaitset=False, repetition=4, device_augmentation=False):
+        withof = _augment.withof(dim, nmods)      # the reference's literal rule (:65-68), on `dim` as the caller spelled it
         if nmods == 1:      # `dim` is one (frames, 60, 60) tuple there (:66-69), the file is allSamples[i][0][0] under datadir[0]
             dim = [tuple(dim)] if not isinstance(dim[0], (tuple, list)) else [tuple(dim[0])]
             datadir = list(datadir[:1])
-        if augmentation_x > 0:
+        if augmentation_x > 0 and not device_augmentation:
             # the reference's default is augmentation_x=1 and its gaitset mains leave it there (mains/mj_trainUWYHGaitNet_
-            # DataGen_CasiaB.py:465): name the argument, the random affine augmentation (:706-728) is not built on this path
+            # DataGen_CasiaB.py:465): the random affine / mirror augmentation (:706-728) runs on the device, but only on request,
+            # so that nobody trains with it without knowing that its parity rests on unpinned readings
             raise NotImplementedError("DataGeneratorGaitMMUWYH on the MI355X path: augmentation_x=%r (random affine / mirror "
-                                      "augmentation, the reference's default) is not implemented; pass augmentation_x=0"
-                                      % (augmentation_x,))
+                                      "augmentation, the reference's default) runs only with device_augmentation=True; pass "
+                                      "device_augmentation=True, or augmentation_x=0 for none" % (augmentation_x,))
         unsupported = [name for name, bad in (("nmods > 3", nmods not in (1, 2, 3)), ("gaitset=False", not gaitset), ("use3D", use3D),
                                               ("isDebug", isDebug), ("softlabel", softlabel), ("use_weights", use_weights),
                                               ("aux_losses", aux_losses), ("triplet_all_fc", triplet_all_fc),
-                                              ("augmentation_x > 0", augmentation_x > 0), ("ntype != 2", ntype != 2)) if bad]
+                                              ("ntype != 2", ntype != 2)) if bad]
         if unsupported:
             raise NotImplementedError("DataGeneratorGaitMMUWYH on the MI355X path: %s not implemented" % ", ".join(unsupported))
         if len(datadir) != nmods or len(dim) != nmods:
@@ -61,7 +65,8 @@ class DataGeneratorGaitMMUWYH(DeviceDataGenerator):
         self.dim, self.n_classes, self.batch_size = dim, n_classes, batch_size
         kept, kept_gait = self._drop_empty(allSamples, gait, datadir)          # __remove_empty_files (:118-146)
         super().__init__(kept, kept_gait, datadir, specs, batch_size, n_classes, labmap=labmap or None, expand_level=expand_level,
-                         repetition=repetition, shuffle=shuffle, is_test=isTest, keep_data=keep_data, single_input=nmods == 1)
+                         repetition=repetition, shuffle=shuffle, is_test=isTest, keep_data=keep_data, single_input=nmods == 1,
+                         augmentation=augmentation_x > 0, withof=withof)
         self.allSamples, self.gait = kept, kept_gait
 
     @staticmethod

@@ -11,8 +11,9 @@ with 2*repetition records each (the P x K batch the batch-all triplet loss wants
 `DeviceDataGenerator` is the `keras.utils.Sequence`-like object `model.fit` takes: it reads the sample files of the chosen
 records (ugaitnet_amd/samples.py), uploads their raw int16 / uint8 arrays once and lets `DeviceBatchAssembler` build the
 expanded, masked fp32 batch in HBM; labels follow `__gen_batchMM` (:764-780, 806-812): `labmap[label]` repeated for every
-expanded row, one-hot beside it.  Augmentation (random affine transforms, :706-728) is not implemented: the generator is the
-reference's with `augmentation_x=0`.
+expanded row, one-hot beside it.  With `augmentation=True` the generator is the reference's with `augmentation_x > 0`: per base
+sample, in batch order, the random affine / mirror parameters are drawn from the sampler's numpy rng (ugaitnet_amd/augment.py) and
+applied on the device by the assembly; without it, the reference's `augmentation_x=0`.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import random as _random
 
 import numpy as np
 
+from . import augment as _augment
 from . import samples as _samples
 from .batching import DeviceBatchAssembler, plan_rows, plan_rows_2mod
 
@@ -91,7 +93,11 @@ class DeviceDataGenerator:
     x_1, use_1, ...] device tensors and y = [labels [rows,1], one-hot [rows,n_classes]] (labels alone when n_classes == 0)."""
 
     def __init__(self, all_samples, gaits, datadirs, specs, batch_size, n_classes, labmap=None, expand_level=2, repetition=4,
-                 shuffle=True, is_test=False, keep_data=False, rng=np.random, mask_rng=_random, device=None, single_input=False):
+                 shuffle=True, is_test=False, keep_data=False, rng=np.random, mask_rng=_random, device=None, single_input=False,
+                 augmentation=False, withof=None):
+        """augmentation: the training generator's random affine / mirror augmentation (the reference's `augmentation_x > 0`), drawn
+        from `rng` as the reference draws from np.random.  withof: the reference's `withof` (augment.withof of the `dim` the caller
+        was given); None -> modality 0 is int16 optical flow."""
         self.all_samples = list(all_samples)
         self.datadirs, self.specs = list(datadirs), list(specs)
         if len(self.datadirs) != len(self.specs):
@@ -107,6 +113,8 @@ class DeviceDataGenerator:
                 raise ValueError("single_input needs exactly one modality")
             self.expand = 1
         self.cache = {} if keep_data else None
+        self.augmentation = bool(augmentation)
+        self.withof = bool(self.specs[0].is_int16 if withof is None else withof)
 
     def __len__(self):
         return len(self.sampler)
@@ -140,9 +148,11 @@ class DeviceDataGenerator:
                     present[i, m] = True
             lb = self.labmap[int(label)] if self.labmap else label
             labels[i * self.expand:(i + 1) * self.expand, 0] = lb
+        # (the augmentation draws come from the numpy rng, the row plan's from `random`: two streams, so their order does not matter)
+        aug = _augment.draw_batch(len(ids), self.withof, self.sampler.rng) if self.augmentation else None
         plan = (plan_rows_2mod if nmod == 2 else plan_rows)(present, self.expand, rng=self.mask_rng)
         X = []
-        for x, u in self.assembler.assemble(raws, plan, present=present):
+        for x, u in self.assembler.assemble(raws, plan, present=present, aug=aug):
             X += [x, u]
         if self.single_input:
             if not present.all():
